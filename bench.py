@@ -8,12 +8,21 @@ kernel.  N GPUs = N independent frames, one per rank (frame sharding, no
 collective on the data path; weak scaling).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4k|1080p-mc|4k-10bit]
-                    [--feed local|rccl] [--no-families] [--no-cpu]
+                    [--feed local|rccl] [--dump-outputs DIR] [--full [--no-families] [--no-cpu] ...]
+
+A plain run does only what the headline needs: it builds the frame, warms up,
+times the K steps and prints the line.  --dump-outputs DIR then also writes
+the picture the last timed step left (rank 0's planes y, u, v as
+DIR/<name>.npy, float32); the frame is seeded, so the same arguments give the
+same inputs in every run.  --full adds everything else the line can carry:
+the bit-exact check against the oracle, the committed rocprofv3 cross-checks,
+the per-launch event-pair diagnostic, the side legs below and the CPU
+baseline (each with its own --no-* switch).
 
 --feed rccl: rank 0 generates every rank's frame and scatters them over RCCL
 point-to-point before the timed region (config 5's coded-block feed over
 xGMI); the feed's time and bytes are reported on their own ("feed").
-At N=1 the line also carries a per-family breakdown ("families": mc-only,
+With --full at N=1 the line also carries a per-family breakdown ("families": mc-only,
 intra-only and itx-only 4K frames of the same bitdepth, one launch each).
 
 Rank 0 prints one JSON line.  See DESIGN.md for the roofline accounting.
@@ -643,12 +652,28 @@ def dry_run(world, rank, local):
         dist.destroy_process_group()
 
 
+def dump_outputs(path, frame):
+    """--dump-outputs: the planes a caller of the timed path receives (the
+    picture the last timed launch wrote), whole, as <path>/y.npy, u.npy and
+    v.npy in float32 (exact for 8- to 16-bit pixels; a 4K 4:2:0 picture is
+    49.8 MB so)."""
+    os.makedirs(path, exist_ok=True)
+    for name, plane in zip(("y", "u", "v"), frame.planes_host()):
+        np.save(os.path.join(path, name + ".npy"), plane.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="4k", choices=sorted(CONFIGS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write rank 0's reconstructed planes of the last step "
+                         "as DIR/y.npy, DIR/u.npy, DIR/v.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the oracle check, the diagnostics, the side legs and the CPU baseline "
+                         "(the --no-* switches below pick among them); off: the headline only")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-check", action="store_true",
                     help="skip the bit-exact check of rank 0's timed frame against the oracle (on by default)")
@@ -673,6 +698,8 @@ def main():
     # agree.  A 1-rank number is never reported under --gpus N > 1
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -749,16 +776,21 @@ def main():
     kern_s = stream_s
     assert kern_s <= my_el / args.steps * (1 + 1e-6), (kern_s, my_el / args.steps)
 
-    # diagnostic only (outside the timed region, not used for frac): an event
-    # pair around each launch; the pairs add their own packets' latency
-    nk = min(args.steps, 100)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(nk)]
-    for a, b in evs:
-        a.record(stream)
-        frame.launch(stream)
-        b.record(stream)
-    torch.cuda.synchronize(dev)
-    pair_s = sum(a.elapsed_time(b) for a, b in evs) * 1e-3 / nk
+    # the picture the last timed step left, before anything else launches
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, frame)
+
+    # diagnostic only (--full; outside the timed region, not used for frac):
+    # an event pair around each launch; the pairs add their own packets' latency
+    nk, pair_s = min(args.steps, 100), None
+    if args.full:
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(nk)]
+        for a, b in evs:
+            a.record(stream)
+            frame.launch(stream)
+            b.record(stream)
+        torch.cuda.synchronize(dev)
+        pair_s = sum(a.elapsed_time(b) for a, b in evs) * 1e-3 / nk
     per_rank = None
     if world > 1:
         per_rank = per_rank_fields([v * 1e6 for v in sh.gather_over_ranks(kern_s, dist, dev)],
@@ -767,7 +799,7 @@ def main():
     # the timed frame's pixels against the oracle (outside the timed region;
     # the launches are idempotent, so the picture is the last step's)
     check = None
-    if not args.no_check and rank == 0:
+    if args.full and not args.no_check and rank == 0:
         orc = ge.load_oracle()
         hf = orc.HostFrame(fd)
         nthr = max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 4))
@@ -778,7 +810,10 @@ def main():
         log(f"[rank 0] bit-exact vs oracle: {check} ({time.perf_counter() - t1:.1f} s on {nthr} threads)")
 
     if rank == 0:
-        traffic, traffic_note = pmc_traffic(cfg.bpc) if args.config in ("4k", "4k-10bit") else (None, None)
+        # (--full) the committed rocprofv3 summaries beside the measured figures
+        traffic, traffic_note = (pmc_traffic(cfg.bpc) if args.full and args.config in ("4k", "4k-10bit")
+                                 else (None, None))
+        rocprof_us = rocprof_kernel_us(cfg.bpc) if args.full and args.config != "1080p-mc" else None
         value = sh.aggregate_gpix_per_s(fd.stats["pixels"], args.steps, world, el)
         bytes_launch = fd.stats["total_bytes"]
         achieved = bytes_launch / kern_s / 1e9
@@ -790,6 +825,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(el / args.steps * 1e3, 5),
+            "full": args.full,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -819,13 +855,13 @@ def main():
                 "kernel_us": round(kern_s * 1e6, 2),
                 "kernel_us_note": "one HIP event pair on the launch stream around the K timed launches "
                                   "(inside the wall-clock bracket, so <= ms_per_step), / K; frac uses it",
-                "event_pair_us_diag": round(pair_s * 1e6, 2),
-                "event_pair_note": f"diagnostic only: mean of {nk} launches each bracketed by its own event "
-                                   "pair (adds the event packets' latency; not used for frac)",
-                "rocprof_kernel_us": rocprof_kernel_us(cfg.bpc) if args.config != "1080p-mc" else None,
-                "frac_rocprof": (round(bytes_launch / (rocprof_kernel_us(cfg.bpc) * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
-                                 if args.config != "1080p-mc" and rocprof_kernel_us(cfg.bpc) else None),
-                "rocprof_source": os.path.relpath(KERNEL_STATS[cfg.bpc], ROOT),
+                "event_pair_us_diag": round(pair_s * 1e6, 2) if pair_s is not None else None,
+                "event_pair_note": f"diagnostic only (--full): mean of {nk} launches each bracketed by its own "
+                                   "event pair (adds the event packets' latency; not used for frac)",
+                "rocprof_kernel_us": rocprof_us,
+                "frac_rocprof": (round(bytes_launch / (rocprof_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
+                                 if rocprof_us else None),
+                "rocprof_source": os.path.relpath(KERNEL_STATS[cfg.bpc], ROOT) if args.full else None,
                 "algorithmic_bytes_per_launch": bytes_launch,
                 "bytes_breakdown": {k: fd.stats[k] for k in
                                     ("ref_bytes", "edge_bytes", "coef_bytes", "dst_bytes", "dst_read_bytes",
@@ -842,29 +878,30 @@ def main():
             out["feed"] = feed
         if per_rank is not None:
             out["per_rank"] = per_rank
-        if not args.no_configs and world == 1 and args.config == "4k":
+        legs = args.full and world == 1   # the side legs: --full at N=1, each with its --no-* switch
+        if not args.no_configs and legs and args.config == "4k":
             out["configs"] = config_legs(dev, stream, args.steps)
-        if not args.no_configs and world == 1 and args.config == "4k":
+        if not args.no_configs and legs and args.config == "4k":
             out["cold_mall"] = cold_mall_leg(fd, dev, stream, args.steps)
-        if not args.no_families and world == 1 and c.get("kind") == "full":
+        if not args.no_families and legs and c.get("kind") == "full":
             out["families"] = family_breakdown(cfg, dev, stream, args.steps)
-        if not args.no_tiles and world == 1:
+        if not args.no_tiles and legs:
             out["tile_batch"] = tile_breakdown(fd, dev, stream, args.steps)
-        if not args.no_intra and world == 1 and c.get("kind") == "full":
+        if not args.no_intra and legs and c.get("kind") == "full":
             out["intra_wavefront"] = intra_breakdown(cfg, dev, stream, args.steps)
-        if not args.no_recorder and world == 1 and c.get("kind") == "full":
+        if not args.no_recorder and legs and c.get("kind") == "full":
             out["recorder"] = recorder_breakdown(cfg, dev)
-        if not args.no_grain and world == 1:
+        if not args.no_grain and legs:
             out["film_grain"] = grain_breakdown(cfg, dev, args.steps)
-        if not args.no_cdef and world == 1:
+        if not args.no_cdef and legs:
             out["cdef"] = cdef_breakdown(cfg, dev, args.steps)
-        if not args.no_superres and world == 1:
+        if not args.no_superres and legs:
             out["superres"] = superres_breakdown(cfg, dev, args.steps)
-        if not args.no_lpf and world == 1:
+        if not args.no_lpf and legs:
             out["loop_filter"] = lpf_breakdown(cfg, dev, args.steps)
-        if not args.no_lr and world == 1:
+        if not args.no_lr and legs:
             out["loop_restoration"] = lr_breakdown(cfg, dev, args.steps)
-        if not args.no_cpu and world == 1:
+        if not args.no_cpu and legs:
             out["cpu_baseline"] = cpu_baseline(fd)
         # (on the unrounded values: the stream events sit inside the wall-clock bracket)
         assert kern_s <= el / args.steps * (1 + 1e-6), "kernel time exceeds the step time"

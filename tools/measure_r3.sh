@@ -25,7 +25,7 @@ for s in $STEPS; do
         ;;
     bench)
         echo "[m] bench" >&2
-        timeout -k 10 600 python3 bench.py > "$O/bench.json" 2> "$O/bench.err" \
+        timeout -k 10 600 python3 bench.py --full > "$O/bench.json" 2> "$O/bench.err" \
             || { echo "bench failed" >&2; tail -20 "$O/bench.err"; exit 1; }
         ;;
     prof)

@@ -19,7 +19,7 @@ run() {
     shift
     echo "[prof] $name" >&2
     timeout -k 10 300 rocprofv3 "$@" -d "$O/$name" -o run --output-format csv -- \
-        python3 "$R/bench.py" --no-cpu $ARGS > "$O/$name.log" 2>&1
+        python3 "$R/bench.py" --full --no-cpu $ARGS > "$O/$name.log" 2>&1
 }
 run trace --kernel-trace --stats
 run fetch --pmc FETCH_SIZE

@@ -31,11 +31,11 @@ for s in "${@:-tests}"; do
     intra) timeout -k 10 600 $PYT -m gpu -x tests/test_gpu_intra_frame.py > "$O/intra.log" 2>&1 || { echo "[r4] intra failed"; exit 1; } ;;
     cdef) timeout -k 10 600 $PYT -m gpu -x tests/test_gpu_cdef.py > "$O/cdef.log" 2>&1 || { echo "[r4] cdef failed"; exit 1; } ;;
     benchpart) # the intra wavefront, CDEF, LR and recorder legs only (recorder host laps on stderr)
-            DAV1D_GPU_REC_TIMING=1 timeout -k 10 600 python -u bench.py --steps 50 --no-families --no-configs --no-tiles \
+            DAV1D_GPU_REC_TIMING=1 timeout -k 10 600 python -u bench.py --full --steps 50 --no-families --no-configs --no-tiles \
                 --no-grain --no-superres --no-lpf --no-cpu --no-check > "$O/benchpart.json" 2> "$O/benchpart.log" \
                 || { echo "[r4] benchpart failed"; exit 1; } ;;
     smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || { echo "[r4] smoke failed"; exit 1; } ;;
-    bench) timeout -k 10 900 python -u bench.py > "$O/bench.json" 2> "$O/bench.log" || { echo "[r4] bench failed"; exit 1; } ;;
+    bench) timeout -k 10 900 python -u bench.py --full > "$O/bench.json" 2> "$O/bench.log" || { echo "[r4] bench failed"; exit 1; } ;;
     benchfast) timeout -k 10 300 python -u bench.py $BENCH_FAST > "$O/benchfast.json" 2> "$O/benchfast.log" || { echo "[r4] benchfast failed"; exit 1; } ;;
     prof) (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run --output-format csv -- python3 "$R/bench.py" --steps 50 $BENCH_FAST) > "$O/prof.log" 2>&1 || { echo "[r4] prof failed"; exit 1; } ;;
     pmc) for c in FETCH_SIZE WRITE_SIZE; do
@@ -44,7 +44,7 @@ for s in "${@:-tests}"; do
     cdefpmc) # CDEF / LR counters: the bench with only those legs (the headline frame runs too; filter by kernel)
          for c in FETCH_SIZE WRITE_SIZE "SQ_INSTS_VALU SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_LDS"; do
              n=$(echo $c | cut -d' ' -f1)
-             (cd /tmp && export TMPDIR=/tmp && timeout -s KILL 150 rocprofv3 --pmc $c -d "$O/cdefpmc_$n" -o run --output-format csv -- python3 "$R/bench.py" --steps 10 --warmup 2 --no-families --no-configs --no-tiles --no-intra --no-recorder --no-grain --no-superres --no-lpf --no-cpu --no-check) > "$O/cdefpmc_$n.log" 2>&1 || { echo "[r4] cdefpmc $n failed"; exit 1; }
+             (cd /tmp && export TMPDIR=/tmp && timeout -s KILL 150 rocprofv3 --pmc $c -d "$O/cdefpmc_$n" -o run --output-format csv -- python3 "$R/bench.py" --full --steps 10 --warmup 2 --no-families --no-configs --no-tiles --no-intra --no-recorder --no-grain --no-superres --no-lpf --no-cpu --no-check) > "$O/cdefpmc_$n.log" 2>&1 || { echo "[r4] cdefpmc $n failed"; exit 1; }
          done ;;
     esac
     echo "[r4] $s done $(date +%T)"

@@ -41,7 +41,7 @@ for s in "${@:-tests}"; do
             [ $rc -le 1 ] || exit 1 ;;
     intra) timeout -k 10 600 $PYT -m gpu -x tests/test_gpu_intra_frame.py > "$O/intra.log" 2>&1 || { echo "[r5] intra failed"; exit 1; } ;;
     benchpart) # the intra wavefront, CDEF, LR and recorder legs only (recorder host laps on stderr)
-            DAV1D_GPU_REC_TIMING=1 timeout -k 10 600 python -u bench.py --steps 50 --no-families --no-configs --no-tiles \
+            DAV1D_GPU_REC_TIMING=1 timeout -k 10 600 python -u bench.py --full --steps 50 --no-families --no-configs --no-tiles \
                 --no-grain --no-superres --no-lpf --no-cpu --no-check > "$O/benchpart.json" 2> "$O/benchpart.log" \
                 || { echo "[r5] benchpart failed"; exit 1; } ;;
     checkasm) # the full checkasm-style space (no --quick), one pass per table and bitdepth
@@ -53,7 +53,7 @@ for s in "${@:-tests}"; do
     ab) # headline-frame A/B of variant libraries (ABV="persist persist2"): kernel us per variant, bit-exact check on
         for v in base $ABV; do
             if [ "$v" = base ]; then unset DAV1D_GPU_LIB_VARIANT; else export DAV1D_GPU_LIB_VARIANT=$v; fi
-            timeout -k 10 300 python -u bench.py --no-families --no-configs --no-tiles --no-intra --no-recorder --no-grain \
+            timeout -k 10 300 python -u bench.py --full --no-families --no-configs --no-tiles --no-intra --no-recorder --no-grain \
                 --no-cdef --no-superres --no-lpf --no-lr --no-cpu --steps ${ABSTEPS:-200} > "$O/ab_$v.json" 2> "$O/ab_$v.log" \
                 || { echo "[r5] ab $v failed"; tail -5 "$O/ab_$v.log"; exit 1; }
             python3 -c "import json; d=json.load(open('$O/ab_$v.json')); r=d['roofline']; print('ab $v', r['kernel_us'], r.get('stream_us_per_step'), d['ms_per_step'], d['config'].get('bit_exact_vs_oracle'))"
@@ -68,12 +68,12 @@ for s in "${@:-tests}"; do
         done
         unset DAV1D_GPU_LIB_VARIANT ;;
     post) # CDEF, LR, super-res and deblocking bench legs (the headline leg runs too)
-        timeout -k 10 400 python -u bench.py --steps 50 --no-families --no-configs --no-tiles --no-intra --no-recorder \
+        timeout -k 10 400 python -u bench.py --full --steps 50 --no-families --no-configs --no-tiles --no-intra --no-recorder \
             --no-grain --no-cpu --no-check > "$O/post.json" 2> "$O/post.log" || { echo "[r5] post failed"; exit 1; }
         python3 -c "import json; d=json.load(open('$O/post.json')); print('post', {k: (d[k]['us_per_frame'], d[k]['bit_exact_vs_oracle']) for k in ('cdef','loop_restoration','superres','loop_filter')})" ;;
     lr) timeout -k 10 600 $PYT -m gpu -x tests/test_gpu_lr.py "tests/test_gpu_checkasm.py::test_checkasm[lr]" tests/test_gpu_chain.py > "$O/lr.log" 2>&1 || { echo "[r5] lr failed"; tail -5 "$O/lr.log"; exit 1; }
         tail -1 "$O/lr.log"
-        timeout -k 10 300 python -u bench.py --steps 50 --no-families --no-configs --no-tiles --no-intra --no-recorder \
+        timeout -k 10 300 python -u bench.py --full --steps 50 --no-families --no-configs --no-tiles --no-intra --no-recorder \
             --no-grain --no-cdef --no-superres --no-lpf --no-cpu --no-check > "$O/lrbench.json" 2> "$O/lrbench.log" \
             || { echo "[r5] lr bench failed"; exit 1; }
         python3 -c "import json; d=json.load(open('$O/lrbench.json'))['loop_restoration']; print('lr', d['us_per_frame'], d['bit_exact_vs_oracle'])" ;;
@@ -88,7 +88,7 @@ for s in "${@:-tests}"; do
             if [ "$v" = base ]; then unset DAV1D_GPU_LIB_VARIANT; else export DAV1D_GPU_LIB_VARIANT=$v; fi
             timeout -k 10 400 $PYT -m gpu -x tests/test_gpu_lr.py tests/test_gpu_chain.py > "$O/ablr_test_$v.log" 2>&1 \
                 || { echo "[r5] ablr tests $v failed"; tail -5 "$O/ablr_test_$v.log"; exit 1; }
-            timeout -k 10 300 python -u bench.py --steps 100 --no-families --no-configs --no-tiles --no-intra --no-recorder \
+            timeout -k 10 300 python -u bench.py --full --steps 100 --no-families --no-configs --no-tiles --no-intra --no-recorder \
                 --no-grain --no-cdef --no-superres --no-lpf --no-cpu > "$O/ablr_$v.json" 2> "$O/ablr_$v.log" \
                 || { echo "[r5] ablr bench $v failed"; exit 1; }
             python3 -c "import json; d=json.load(open('$O/ablr_$v.json'))['loop_restoration']; print('ablr $v', d['us_per_frame'], d['bit_exact_vs_oracle'], '$(tail -1 "$O/ablr_test_$v.log" | tr -d =)')"
@@ -99,7 +99,7 @@ for s in "${@:-tests}"; do
             if [ "$v" = base ]; then unset DAV1D_GPU_LIB_VARIANT; else export DAV1D_GPU_LIB_VARIANT=$v; fi
             timeout -k 10 400 $PYT -m gpu -x tests/test_gpu_cdef.py > "$O/abcdef_test_$v.log" 2>&1 \
                 || { echo "[r5] abcdef tests $v failed"; tail -5 "$O/abcdef_test_$v.log"; exit 1; }
-            timeout -k 10 300 python -u bench.py --steps 100 --no-families --no-configs --no-tiles --no-intra --no-recorder \
+            timeout -k 10 300 python -u bench.py --full --steps 100 --no-families --no-configs --no-tiles --no-intra --no-recorder \
                 --no-grain --no-lr --no-superres --no-lpf --no-cpu > "$O/abcdef_$v.json" 2> "$O/abcdef_$v.log" \
                 || { echo "[r5] abcdef bench $v failed"; exit 1; }
             python3 -c "import json; d=json.load(open('$O/abcdef_$v.json'))['cdef']; print('abcdef $v', d['us_per_frame'], d['bit_exact_vs_oracle'], '$(tail -1 "$O/abcdef_test_$v.log" | tr -d =)')"
@@ -107,7 +107,7 @@ for s in "${@:-tests}"; do
         unset DAV1D_GPU_LIB_VARIANT ;;
     flowunits) # the wavefront's units-per-task cap above level 0 (DAV1D_GPU_FLOW_UNITS), 4K intra frames
         for U in ${FLOWU:-4 8 16}; do
-            DAV1D_GPU_FLOW_UNITS=$U timeout -k 10 300 python -u bench.py --steps 20 --no-families --no-configs --no-tiles --no-recorder --no-grain \
+            DAV1D_GPU_FLOW_UNITS=$U timeout -k 10 300 python -u bench.py --full --steps 20 --no-families --no-configs --no-tiles --no-recorder --no-grain \
                 --no-cdef --no-superres --no-lpf --no-lr --no-cpu --no-check > "$O/flowunits_$U.json" 2> "$O/flowunits_$U.log" \
                 || { echo "[r5] flowunits $U failed"; exit 1; }
             python3 -c "import json; d=json.load(open('$O/flowunits_$U.json'))['intra_wavefront']; print('flowunits $U', d['1_tile']['ms_per_frame'], d['1_tile']['bit_exact_vs_oracle'], d['2x2_tiles']['ms_per_frame'], d['2x2_tiles']['bit_exact_vs_oracle'])"
@@ -115,7 +115,7 @@ for s in "${@:-tests}"; do
     abintra) # the intra wavefront bench leg per variant library (ABV): 1-tile / 2x2 ms per 4K frame, bit-exact
         for v in base $ABV; do
             if [ "$v" = base ]; then unset DAV1D_GPU_LIB_VARIANT; else export DAV1D_GPU_LIB_VARIANT=$v; fi
-            timeout -k 10 400 python -u bench.py --steps 20 --no-families --no-configs --no-tiles --no-recorder --no-grain \
+            timeout -k 10 400 python -u bench.py --full --steps 20 --no-families --no-configs --no-tiles --no-recorder --no-grain \
                 --no-cdef --no-superres --no-lpf --no-lr --no-cpu --no-check > "$O/abintra_$v.json" 2> "$O/abintra_$v.log" \
                 || { echo "[r5] abintra $v failed"; tail -5 "$O/abintra_$v.log"; exit 1; }
             python3 -c "import json; d=json.load(open('$O/abintra_$v.json'))['intra_wavefront']; print('abintra $v', d['1_tile']['ms_per_frame'], d['1_tile']['bit_exact_vs_oracle'], d['2x2_tiles']['ms_per_frame'], d['2x2_tiles']['bit_exact_vs_oracle'])"
@@ -123,12 +123,12 @@ for s in "${@:-tests}"; do
         unset DAV1D_GPU_LIB_VARIANT ;;
     cdef) timeout -k 10 600 $PYT -m gpu -x tests/test_gpu_cdef.py "tests/test_gpu_checkasm.py::test_checkasm[cdef]" > "$O/cdef.log" 2>&1 || { echo "[r5] cdef failed"; tail -5 "$O/cdef.log"; exit 1; }
         tail -1 "$O/cdef.log"
-        timeout -k 10 300 python -u bench.py --steps 50 --no-families --no-configs --no-tiles --no-intra --no-recorder \
+        timeout -k 10 300 python -u bench.py --full --steps 50 --no-families --no-configs --no-tiles --no-intra --no-recorder \
             --no-grain --no-lr --no-superres --no-lpf --no-cpu --no-check > "$O/cdefbench.json" 2> "$O/cdefbench.log" \
             || { echo "[r5] cdef bench failed"; exit 1; }
         python3 -c "import json; d=json.load(open('$O/cdefbench.json'))['cdef']; print('cdef', d['us_per_frame'], d['bit_exact_vs_oracle'])" ;;
     smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || { echo "[r5] smoke failed"; exit 1; } ;;
-    bench) timeout -k 10 900 python -u bench.py > "$O/bench.json" 2> "$O/bench.log" || { echo "[r5] bench failed"; exit 1; } ;;
+    bench) timeout -k 10 900 python -u bench.py --full > "$O/bench.json" 2> "$O/bench.log" || { echo "[r5] bench failed"; exit 1; } ;;
     benchfast) timeout -k 10 300 python -u bench.py $BENCH_FAST > "$O/benchfast.json" 2> "$O/benchfast.log" || { echo "[r5] benchfast failed"; exit 1; } ;;
     prof) (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run --output-format csv -- python3 "$R/bench.py" --steps 50 $BENCH_FAST) > "$O/prof.log" 2>&1 || { echo "[r5] prof failed"; exit 1; } ;;
     prof10) (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/prof10" -o run --output-format csv -- python3 "$R/bench.py" --config 4k-10bit --steps 50 $BENCH_FAST) > "$O/prof10.log" 2>&1 || { echo "[r5] prof10 failed"; exit 1; }
@@ -143,7 +143,7 @@ for s in "${@:-tests}"; do
     cdefpmc) # CDEF / LR counters: the bench with only those legs (the headline frame runs too; filter by kernel)
          for c in FETCH_SIZE WRITE_SIZE "SQ_INSTS_VALU SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_LDS"; do
              n=$(echo $c | cut -d' ' -f1)
-             (cd /tmp && export TMPDIR=/tmp && timeout -s KILL 150 rocprofv3 --pmc $c -d "$O/cdefpmc_$n" -o run --output-format csv -- python3 "$R/bench.py" --steps 10 --warmup 2 --no-families --no-configs --no-tiles --no-intra --no-recorder --no-grain --no-superres --no-lpf --no-cpu --no-check) > "$O/cdefpmc_$n.log" 2>&1 || { echo "[r5] cdefpmc $n failed"; exit 1; }
+             (cd /tmp && export TMPDIR=/tmp && timeout -s KILL 150 rocprofv3 --pmc $c -d "$O/cdefpmc_$n" -o run --output-format csv -- python3 "$R/bench.py" --full --steps 10 --warmup 2 --no-families --no-configs --no-tiles --no-intra --no-recorder --no-grain --no-superres --no-lpf --no-cpu --no-check) > "$O/cdefpmc_$n.log" 2>&1 || { echo "[r5] cdefpmc $n failed"; exit 1; }
          done ;;
     esac
     echo "[r5] $s done $(date +%T)"

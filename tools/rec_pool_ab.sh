@@ -1,5 +1,5 @@
 mkdir -p gpurun_out/r5t
-F="--steps 20 --no-families --no-configs --no-tiles --no-intra --no-grain --no-cdef --no-superres --no-lpf --no-lr --no-cpu"
+F="--full --steps 20 --no-families --no-configs --no-tiles --no-intra --no-grain --no-cdef --no-superres --no-lpf --no-lr --no-cpu"
 for i in 1 2; do
   DAV1D_GPU_REC_THREADS=8 timeout -k 10 300 python -u bench.py $F > gpurun_out/r5t/rec8_$i.json 2> gpurun_out/r5t/rec8_$i.log || exit 1
   timeout -k 10 300 python -u bench.py $F > gpurun_out/r5t/recauto_$i.json 2> gpurun_out/r5t/recauto_$i.log || exit 1

@@ -11,8 +11,8 @@ for v in ${VARIANTS:-b16 b8 b32 b64 raster}; do
     esac
     O=$R/gpurun_out/wa_$v
     mkdir -p "$O"
-    timeout -s KILL 150 rocprofv3 --pmc WRITE_SIZE -d "$O/write" -o run --output-format csv -- python3 "$R/bench.py" $A > "$O/write.log" 2>&1 || exit 1
-    timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE -d "$O/fetch" -o run --output-format csv -- python3 "$R/bench.py" $A > "$O/fetch.log" 2>&1 || exit 1
-    timeout -s KILL 150 rocprofv3 --kernel-trace --stats -d "$O/trace" -o run --output-format csv -- python3 "$R/bench.py" $A > "$O/trace.log" 2>&1 || exit 1
+    timeout -s KILL 150 rocprofv3 --pmc WRITE_SIZE -d "$O/write" -o run --output-format csv -- python3 "$R/bench.py" --full $A > "$O/write.log" 2>&1 || exit 1
+    timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE -d "$O/fetch" -o run --output-format csv -- python3 "$R/bench.py" --full $A > "$O/fetch.log" 2>&1 || exit 1
+    timeout -s KILL 150 rocprofv3 --kernel-trace --stats -d "$O/trace" -o run --output-format csv -- python3 "$R/bench.py" --full $A > "$O/trace.log" 2>&1 || exit 1
     echo "[wa] $v done" >&2
 done
