@@ -177,6 +177,26 @@ class FilmGrainBatch(ctypes.Structure):
                 ("scratch", ctypes.c_void_p)]
 
 
+class FilmGrainDSPContext(ctypes.Structure):
+    """Dav1dFilmGrainDSPContext_{8bpc,16bpc} (src/filmgrain.h:74-80): eight
+    function pointers, the same slots at both bit depths."""
+    _fields_ = [("generate_grain_y", ctypes.c_void_p), ("generate_grain_uv", ctypes.c_void_p * 3),
+                ("fgy_32x32xn", ctypes.c_void_p), ("fguv_32x32xn", ctypes.c_void_p * 3)]
+
+
+def film_grain_fn_types(bpc):
+    """ctypes prototypes of the table's entries (src/filmgrain.h:46-72):
+    (generate_grain_y, generate_grain_uv, fgy_32x32xn, fguv_32x32xn); the
+    16 bpc ones take a trailing bitdepth_max."""
+    VP, I, D = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(FilmGrainData)
+    hbd = [] if bpc == 8 else [I]
+    return (ctypes.CFUNCTYPE(None, VP, D, *hbd),
+            ctypes.CFUNCTYPE(None, VP, VP, D, ctypes.c_ssize_t, *hbd),
+            ctypes.CFUNCTYPE(None, VP, VP, ctypes.c_ssize_t, D, ctypes.c_size_t, VP, VP, I, I, *hbd),
+            ctypes.CFUNCTYPE(None, VP, VP, ctypes.c_ssize_t, D, ctypes.c_size_t, VP, VP, I, I, VP, ctypes.c_ssize_t,
+                             I, I, *hbd))
+
+
 class CdefFrame(ctypes.Structure):
     """Dav1dGpuCdefFrame: one frame of bytefn(dav1d_cdef_brow) work."""
     _fields_ = [("in_", Plane * 3), ("out", Plane * 3), ("cdef_idx", ctypes.c_void_p), ("noskip", ctypes.c_void_p),
@@ -302,6 +322,17 @@ def load_lib():
             f = getattr(L, f"dav1d_gpu_apply_grain_{bpc}bpc")
             f.argtypes = [ctypes.POINTER(FilmGrainBatch), ctypes.c_void_p]
             f.restype = ctypes.c_int
+            f = getattr(L, f"dav1d_gpu_prep_grain_{bpc}bpc")
+            f.argtypes = [ctypes.POINTER(FilmGrainData), ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                          ctypes.c_void_p]
+            f.restype = ctypes.c_int
+            f = getattr(L, f"dav1d_gpu_apply_grain_rows_{bpc}bpc")
+            f.argtypes = [ctypes.POINTER(FilmGrainBatch), ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+            f.restype = ctypes.c_int
+            for hook in ("dav1d_film_grain_dsp_init", "dav1d_film_grain_dsp_init_gpu"):
+                f = getattr(L, f"{hook}_{bpc}bpc")
+                f.argtypes = [ctypes.POINTER(FilmGrainDSPContext)]
+                f.restype = None
         for bpc in (8, 16):
             f = getattr(L, f"dav1d_gpu_lr_frame_{bpc}bpc")
             f.argtypes = [ctypes.POINTER(LrFrame), ctypes.c_void_p]
@@ -373,6 +404,10 @@ EXPORTED_SYMBOLS = [
     "dav1d_gpu_recorder_prep_ms",
     "dav1d_gpu_recorder_set_top_edge",
     "dav1d_gpu_apply_grain_8bpc", "dav1d_gpu_apply_grain_16bpc",
+    "dav1d_gpu_prep_grain_8bpc", "dav1d_gpu_prep_grain_16bpc",
+    "dav1d_gpu_apply_grain_rows_8bpc", "dav1d_gpu_apply_grain_rows_16bpc",
+    "dav1d_film_grain_dsp_init_8bpc", "dav1d_film_grain_dsp_init_16bpc",
+    "dav1d_film_grain_dsp_init_gpu_8bpc", "dav1d_film_grain_dsp_init_gpu_16bpc",
     "dav1d_cdef_dsp_init_8bpc", "dav1d_cdef_dsp_init_16bpc",
     "dav1d_cdef_dsp_init_gpu_8bpc", "dav1d_cdef_dsp_init_gpu_16bpc",
     "dav1d_gpu_cdef_frame_8bpc", "dav1d_gpu_cdef_frame_16bpc",

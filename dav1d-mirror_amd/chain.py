@@ -4,7 +4,8 @@ what dav1d_filter_sbrow runs per superblock row (src/recon_tmpl.c:2104-2160,
 driven from src/decode.c / thread_task.c) -- deblocking
 (dav1d_gpu_loopfilter_frame_*), CDEF (dav1d_gpu_cdef_frame_*), loop
 restoration (dav1d_gpu_lr_frame_*) -- and film grain on the output picture
-(dav1d_gpu_apply_grain_*, src/fg_apply_tmpl.c:222-241).
+(dav1d_gpu_apply_grain_*, src/fg_apply_tmpl.c:222-241, or prepped on a side
+stream and applied per 32-row strip behind LR, `launch_per_row_grain`).
 
 Pictures are allocated the way dav1d's picture allocator does (128-aligned
 width and height, src/picture.c:49-66), so every stage reads and writes the
@@ -102,6 +103,54 @@ class DeviceChain:
         self.cdef.launch(s, rows=(rows[-1], rows[-1] + step))
         self.lr.launch(s, rows=(rows[-1], rows[-1] + step))
         self.grain.launch(s)
+
+    def launch_per_row_grain(self, stream=None, step=64):
+        """launch_per_row with film grain in the loop, as a decoder that
+        preps at the frame header and applies grain per strip behind the
+        loop restoration (dav1d_prep_grain / dav1d_apply_grain_row,
+        src/fg_apply_tmpl.c:100-223): the LUTs are built on a side stream
+        from the start, the main stream waits for them before its first
+        strip; after LR of rows [y - step, y) the restored rows reach
+        y - 8, so the 32-row strips ending at or above it run, and the rest
+        after the last LR range."""
+        torch = self.torch
+        s = stream if stream is not None else torch.cuda.current_stream()
+        if getattr(self, "_grain_side", None) is None:
+            self._grain_side = torch.cuda.Stream(device=self.A[0].device)
+            self._grain_ready, self._grain_done = torch.cuda.Event(), None
+        if self._grain_done is not None:   # the previous call's strips still read the scratch
+            self._grain_side.wait_event(self._grain_done)
+        else:   # the first call: the scratch's zero fill may still be pending on `s`
+            self._grain_side.wait_stream(s)
+        self.grain.launch_prep(self._grain_side)
+        self._grain_ready.record(self._grain_side)
+        self.recon.launch(s)
+        strips, done, waited = self.grain.strips, 0, False
+
+        def grain_upto(n):
+            nonlocal done, waited
+            n = min(n, strips)
+            if n <= done:
+                return
+            if not waited:
+                s.wait_event(self._grain_ready)
+                waited = True
+            self.grain.launch_rows(done, n, s)
+            done = n
+
+        rows = list(range(0, self.fd.cfg.height, step))
+        for k, y in enumerate(rows):
+            self.lpf.launch(s, rows=(y, y + step))
+            if k:
+                self.cdef.launch(s, rows=(y - step, y))
+                self.lr.launch(s, rows=(y - step, y))
+                grain_upto((y - 8) // 32)
+        self.cdef.launch(s, rows=(rows[-1], rows[-1] + step))
+        self.lr.launch(s, rows=(rows[-1], rows[-1] + step))
+        grain_upto(strips)
+        if self._grain_done is None:
+            self._grain_done = torch.cuda.Event()
+        self._grain_done.record(s)
 
     def stage_host(self, P):
         out = []

@@ -1,6 +1,10 @@
 // grain.hip -- film grain synthesis on the device (SURVEY 8(f) row 4;
 // include/dav1d_gpu.h, Dav1dGpuFilmGrainBatch): bitfn(dav1d_apply_grain)
-// (src/fg_apply_tmpl.c:222-241) for a whole picture in two launches.
+// (src/fg_apply_tmpl.c:222-241) for a whole picture in two launches, the two
+// launches on their own (dav1d_gpu_prep_grain_*, dav1d_gpu_apply_grain_rows_*
+// for a range of 32-row strips: dav1d_prep_grain / dav1d_apply_grain_row,
+// :100-223) and, on the same device code, the per-call table
+// Dav1dFilmGrainDSPContext (src/filmgrain.h:46-80).
 //
 // k_grain_prep (one 256-thread workgroup): the grain LUTs of
 // generate_grain_y / generate_grain_uv (src/filmgrain_tmpl.c:51-144) and the
@@ -27,6 +31,7 @@
 
 #include "dav1d_gpu.h"
 #include "dsp_common.hpp"
+#include "runtime.hpp"
 
 namespace dgpu {
 
@@ -202,6 +207,46 @@ __device__ void ar_sweep(int16_t (*g)[kGW], const int16_t (*gy)[kGW], const int8
     if (p == 0 && lane == 0) __hip_atomic_store(luma_done, 1 << 30, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// k_grain_gen's steps 1 and 2 (k_grain_prep's, for one plane by one wave).
+// Plane p's white noise (filmgrain_tmpl.c:59-68 / 100-108): the plane zeroed,
+// then 96 draws per lane
+__device__ __forceinline__ void prep_fill(int16_t (*g)[kGW], const Dav1dGpuFilmGrainData &d, int p, int cw, int ch,
+                                          int bd8, int lane) {
+    for (int i = lane; i < kGH * kGW; i += 64) (&g[0][0])[i] = 0;
+    unsigned s = d.seed ^ (p == 0 ? 0u : p == 1 ? 0xb524u : 0x49d8u);
+    for (int j = 0; j < lane; j++) {   // seed advanced lane * 96 steps
+        unsigned t = 0;
+        for (int b = 0; b < 16; b++)
+            if ((s >> b) & 1) t ^= c_jump96[b];
+        s = t;
+    }
+    const int shift = 4 - bd8 + d.grain_scale_shift;
+    const int n = cw * ch;
+    for (int k = 0; k < kChunk; k++) {
+        const int i = lane * kChunk + k;
+        const int v = fg_rand(11, s);
+        if (i < n) g[i / cw][i % cw] = (int16_t)rnd2(dspt_gaussian[v], shift);
+    }
+}
+
+// Plane p's auto-regressive filter by one wave, anti-diagonal sweeps (x + 4y)
+__device__ __forceinline__ void prep_ar(int16_t (*g)[kGW], const int16_t (*gy)[kGW], const Dav1dGpuFilmGrainData &d,
+                                        int p, int cw, int ch, int sx, int sy, int bd8, int lane, int *luma_done) {
+    const int gmin = -(128 << bd8), gmax = (128 << bd8) - 1;
+    const int8_t *cf = p == 0 ? d.ar_coeffs_y : d.ar_coeffs_uv[p - 1];
+    const int ny = d.num_y_points, sh = (int)d.ar_coeff_shift;
+    switch (d.ar_coeff_lag) {
+        case 0: ar_sweep<0>(g, gy, cf, p, cw, ch, sx, sy, ny, sh, gmin, gmax, lane, luma_done); break;
+        case 1: ar_sweep<1>(g, gy, cf, p, cw, ch, sx, sy, ny, sh, gmin, gmax, lane, luma_done); break;
+        case 2: ar_sweep<2>(g, gy, cf, p, cw, ch, sx, sy, ny, sh, gmin, gmax, lane, luma_done); break;
+        default: ar_sweep<3>(g, gy, cf, p, cw, ch, sx, sy, ny, sh, gmin, gmax, lane, luma_done); break;
+    }
+}
+
+// (The body below is kept as one piece: the luma sweep is the critical path of
+// the whole film grain entry and its code is sensitive to how the kernel is
+// put together.  k_grain_gen uses prep_fill / prep_ar above, which restate
+// steps 1 and 2 for one plane; ar_sweep is shared.)
 __global__ __launch_bounds__(256) void k_grain_prep(GrainArgs a) {
     __shared__ int16_t g[3][kGH][kGW];
     __shared__ int luma_done;
@@ -267,6 +312,30 @@ __global__ __launch_bounds__(256) void k_grain_prep(GrainArgs a) {
     }
 }
 
+// generate_grain_y / generate_grain_uv of the per-call tier: the prep body
+// for one plane by one wave.  Chroma reads the caller's luma grain (buf_y,
+// [73][82] contiguous; NULL when there is no luma term).  Writes rows
+// [0, ch) by columns [0, cw) of `out` (pitch `op` entries), the extent the
+// reference writes (filmgrain_tmpl.c:59-68 / 100-108).
+template <typename E>
+__global__ __launch_bounds__(64) void k_grain_gen(GrainArgs a, int p, const E *buf_y, E *out, int op) {
+    __shared__ int16_t g[2][kGH][kGW];   // [0] luma grain, [1] the chroma plane
+    __shared__ int luma_done;
+    const Dav1dGpuFilmGrainData &d = a.d;
+    const int lane = threadIdx.x, bd8 = bd8_of(a.bdmax);
+    const int sx = a.layout != 3, sy = a.layout == 1;
+    const int cw = p && sx ? 44 : kGW, ch = p && sy ? 38 : kGH;
+    int16_t (*gp)[kGW] = p ? g[1] : g[0];
+    if (lane == 0) luma_done = p ? 1 << 30 : 0;   // chroma: the luma grain is final
+    if (p)
+        for (int i = lane; i < kGH * kGW; i += 64) (&g[0][0][0])[i] = buf_y ? (int16_t)buf_y[i] : (int16_t)0;
+    prep_fill(gp, d, p, cw, ch, bd8, lane);
+    __syncthreads();
+    prep_ar(gp, g[0], d, p, cw, ch, sx, sy, bd8, lane, &luma_done);
+    __syncthreads();
+    for (int i = lane; i < ch * cw; i += 64) out[(i / cw) * op + i % cw] = (E)gp[i / cw][i % cw];
+}
+
 template <int BPC> struct ApplyArgs {
     using P = typename Px<BPC>::pixel;
     const P *in[3];
@@ -274,9 +343,21 @@ template <int BPC> struct ApplyArgs {
     int is[3], os[3];   // strides, pixels
     int w, h, layout, bdmax, is_id;
     Dav1dGpuFilmGrainData d;
-    const int16_t *grain;
-    const uint8_t *scaling;
+    const int16_t *grain;     // [3][73][82] (the scratch)
+    const uint8_t *scaling;   // [3][4096]
+    // kApplyRows, kApplyCall: the 32-luma-row strips [row0, row0 + nrows) of the launch
+    int row0, nrows;
+    // kApplyCall: one plane `plane` of one strip; the plane pointers start at
+    // the strip's first row, the caller's LUTs for that plane
+    int plane;
+    const int16_t *call_grain;     // [73][82]
+    const uint8_t *call_scaling;   // 256 / 4096 entries
 };
+
+// What a launch of k_grain_apply covers.  The whole-picture instance is the
+// code of the one-call entry (every strip, no offsets); the others add what
+// their entries need, so that entry's kernels do not pay for it.
+enum { kApplyPicture = 0, kApplyRows = 1, kApplyCall = 2 };
 
 // the row seed's offset for block column c: the (c+1)-th 8-bit draw
 // (fgy_32x32xn, filmgrain_tmpl.c:187-205), by jump-ahead
@@ -307,11 +388,14 @@ template <int BPC, int NP> struct PlaneJob {
     P *dst;
     int sv[NP], lv[NP];
 
+    template <int MODE>
     __device__ __forceinline__ void load(const ApplyArgs<BPC> &a, int pl_, int c_, int row_) {
         const Dav1dGpuFilmGrainData &d = a.d;
         pl = pl_;
         c = c_;
         row = row_;
+        grained = false;
+        if (MODE == kApplyCall && pl != a.plane) return;   // not the call's plane: nothing read or written
         const int sx = a.layout != 3, sy = a.layout == 1;
         ssx = pl ? sx : 0;
         ssy = pl ? sy : 0;
@@ -320,7 +404,7 @@ template <int BPC, int NP> struct PlaneJob {
         bh0 = 32 >> ssy;
         lw = 5 - ssx;
         x0 = c * bw0;
-        const int y0 = row * bh0;
+        const int y0 = MODE == kApplyCall ? 0 : row * bh0;
         bw = min(bw0, pw - x0);
         const int lrows = min(32, a.h - row * 32);
         bh = pl ? (lrows + ssy) >> ssy : lrows;
@@ -329,7 +413,7 @@ template <int BPC, int NP> struct PlaneJob {
         src = (pl == 0 ? a.in[0] : pl == 1 ? a.in[1] : a.in[2]) + (size_t)y0 * is + x0;
         dst = (pl == 0 ? a.out[0] : pl == 1 ? a.out[1] : a.out[2]) + (size_t)y0 * os + x0;
         grained = pl ? (d.chroma_scaling_from_luma || d.num_uv_points[pl - 1]) : d.num_y_points;
-        const P *luma = a.in[0] + (size_t)(row * 32) * a.is[0];
+        const P *luma = a.in[0] + (MODE == kApplyCall ? (size_t)0 : (size_t)(row * 32) * a.is[0]);
 #pragma unroll
         for (int k = 0; k < NP; k++) {
             const int i = threadIdx.x + 256 * k, y = i >> lw, x = i & (bw0 - 1);
@@ -346,12 +430,13 @@ template <int BPC, int NP> struct PlaneJob {
         }
     }
 
+    template <int MODE>
     __device__ __forceinline__ void finish(const ApplyArgs<BPC> &a, const int (&off)[2][2], const uint8_t *sc) {
         if (!grained) return;
         const Dav1dGpuFilmGrainData &d = a.d;
         const int bd8 = bd8_of(a.bdmax);
         const int gmin = -(128 << bd8), gmax = (128 << bd8) - 1;
-        const int16_t *g = a.grain + pl * kGH * kGW;
+        const int16_t *g = MODE == kApplyCall ? a.call_grain : a.grain + pl * kGH * kGW;
         int vmin = 0, vmax = a.bdmax;
         if (d.clip_to_restricted_range) {
             vmin = 16 << bd8;
@@ -402,66 +487,122 @@ template <int BPC, int NP> struct PlaneJob {
     }
 };
 
-template <int BPC, int LAYOUT>
+template <int BPC, int LAYOUT, int MODE>
 __global__ __launch_bounds__(256) void k_grain_apply(ApplyArgs<BPC> a) {
     constexpr int SC = BPC == 8 ? 256 : 4096;
     constexpr int NPC = LAYOUT == 1 ? 1 : LAYOUT == 2 ? 2 : 4;   // chroma pixels per thread
     __shared__ int off[2][2];   // [column: this, previous][row: this, previous]
-    __shared__ uint8_t sc[3][SC];
+    __shared__ uint8_t sc[LAYOUT == 0 || MODE == kApplyCall ? 1 : 3][SC];
     const Dav1dGpuFilmGrainData &d = a.d;
     // XCD-contiguous block order: workgroups are dealt round-robin over the
     // 8 XCDs, so logical block (b % 8) * (nb / 8) + b / 8 gives each XCD a
     // contiguous run of blocks; a 128-B picture line (4 blocks of one row)
     // is then read and written through one L2 instead of four
-    const int cols = (a.w + 31) >> 5, nblk = cols * ((a.h + 31) >> 5);
+    // kApplyRows / kApplyCall: the grid holds the blocks of the launch's strips
+    // only; a block's seeds and overlap still use its row in the picture.
+    const int cols = (a.w + 31) >> 5, nblk = cols * (MODE == kApplyPicture ? (a.h + 31) >> 5 : a.nrows);
     const int nb8 = (int)gridDim.x >> 3, b = blockIdx.x;
     const int lb = (b & 7) * nb8 + (b >> 3);
     if (lb >= nblk) return;
-    const int c = lb % cols, row = lb / cols;
+    const int c = lb % cols, row = (MODE == kApplyPicture ? 0 : a.row0) + lb / cols;
     // the picture loads of all three planes first (they need no offsets)
     PlaneJob<BPC, 4> jy;
-    PlaneJob<BPC, NPC> ju, jv;
-    jy.load(a, 0, c, row);
-    ju.load(a, 1, c, row);
-    jv.load(a, 2, c, row);
+    PlaneJob<BPC, NPC> ju, jv;   // (LAYOUT 0, I400: luma only, never loaded)
+    jy.template load<MODE>(a, 0, c, row);
+    if constexpr (LAYOUT != 0) {
+        ju.template load<MODE>(a, 1, c, row);
+        jv.template load<MODE>(a, 2, c, row);
+    }
     if (threadIdx.x < 4) {
         const int bc = threadIdx.x & 1, br = threadIdx.x >> 1;
         const bool used = (!bc || (d.overlap_flag && c)) && (!br || (d.overlap_flag && row));
         off[bc][br] = used ? fg_offset(d.seed, row - br, c - bc) : 0;
     }
-    for (int i = threadIdx.x * 4; i < 3 * SC; i += 1024)   // the scaling LUTs (4 KB apart in the scratch)
-        *reinterpret_cast<uint32_t *>(&sc[0][0] + i) =
-            *reinterpret_cast<const uint32_t *>(a.scaling + (i / SC) * 4096 + (i % SC));
+    if constexpr (MODE == kApplyCall) {   // the one scaling LUT the call's plane looks up
+        for (int i = threadIdx.x * 4; i < SC; i += 1024)
+            *reinterpret_cast<uint32_t *>(&sc[0][0] + i) = *reinterpret_cast<const uint32_t *>(a.call_scaling + i);
+    } else {
+        for (int i = threadIdx.x * 4; i < (LAYOUT == 0 ? 1 : 3) * SC; i += 1024)   // the scaling LUTs (4 KB apart in the scratch)
+            *reinterpret_cast<uint32_t *>(&sc[0][0] + i) =
+                *reinterpret_cast<const uint32_t *>(a.scaling + (i / SC) * 4096 + (i % SC));
+    }
     __syncthreads();
     int o[2][2] = {{off[0][0], off[0][1]}, {off[1][0], off[1][1]}};
-    jy.finish(a, o, sc[0]);
-    ju.finish(a, o, d.chroma_scaling_from_luma ? sc[0] : sc[1]);
-    jv.finish(a, o, d.chroma_scaling_from_luma ? sc[0] : sc[2]);
+    if constexpr (MODE == kApplyCall) {
+        jy.template finish<MODE>(a, o, sc[0]);
+        if constexpr (LAYOUT != 0) {
+            ju.template finish<MODE>(a, o, sc[0]);
+            jv.template finish<MODE>(a, o, sc[0]);
+        }
+    } else {
+        jy.template finish<MODE>(a, o, sc[0]);
+        if constexpr (LAYOUT != 0) {
+            ju.template finish<MODE>(a, o, d.chroma_scaling_from_luma ? sc[0] : sc[1]);
+            jv.template finish<MODE>(a, o, d.chroma_scaling_from_luma ? sc[0] : sc[2]);
+        }
+    }
 }
 
+static int launch_failed(const char *what) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return 0;
+    fprintf(stderr, "dav1d-gpu: film grain %s launch failed: %s\n", what, hipGetErrorString(e));
+    return -3;
+}
+
+// one workgroup per 32x32 luma block of the launch's strips
+template <int BPC, int MODE>
+static void launch_apply(const ApplyArgs<BPC> &a, hipStream_t stream) {
+    const int nblk = ((a.w + 31) / 32) * (MODE == kApplyPicture ? (a.h + 31) / 32 : a.nrows);
+    const dim3 grid((unsigned)((nblk + 7) & ~7));
+    switch (a.layout) {
+    case 0: k_grain_apply<BPC, 0, MODE><<<grid, 256, 0, stream>>>(a); break;
+    case 1: k_grain_apply<BPC, 1, MODE><<<grid, 256, 0, stream>>>(a); break;
+    case 2: k_grain_apply<BPC, 2, MODE><<<grid, 256, 0, stream>>>(a); break;
+    default: k_grain_apply<BPC, 3, MODE><<<grid, 256, 0, stream>>>(a); break;
+    }
+}
+
+// dav1d_gpu_prep_grain_*: k_grain_prep alone (no picture is touched)
 template <int BPC>
-static int launch_grain(const Dav1dGpuFilmGrainBatch *b, hipStream_t stream) {
+static int launch_prep(const Dav1dGpuFilmGrainData *data, int layout, int bitdepth_max, void *scratch,
+                       hipStream_t stream) {
+    if (!data || !scratch || layout < 0 || layout > 3) return -1;
+    GrainArgs g;
+    memset(&g, 0, sizeof(g));
+    g.d = *data;
+    g.layout = layout;
+    g.bdmax = BPC == 8 ? 255 : bitdepth_max;
+    g.grain = (int16_t *)scratch;
+    g.scaling = (uint8_t *)scratch + 3 * kGH * kGW * 2;
+    if (g.d.ar_coeff_lag < 0 || g.d.ar_coeff_lag > 3 || g.d.num_y_points < 0 || g.d.num_y_points > 14 ||
+        g.d.num_uv_points[0] < 0 || g.d.num_uv_points[0] > 10 || g.d.num_uv_points[1] < 0 ||
+        g.d.num_uv_points[1] > 10)
+        return -1;
+    if (layout == 0) {   // I400: no chroma, its LUTs are written as zeros
+        g.d.chroma_scaling_from_luma = 0;
+        g.d.num_uv_points[0] = g.d.num_uv_points[1] = 0;
+    }
+    k_grain_prep<<<1, 256, 0, stream>>>(g);
+    return launch_failed("prep");
+}
+
+// dav1d_gpu_apply_grain_rows_*: the apply kernel over the strips [r0, r1)
+// (whole: every strip, from the one-call entry, with the whole-picture instance)
+template <int BPC>
+static int launch_rows(const Dav1dGpuFilmGrainBatch *b, int r0, int r1, hipStream_t stream, bool whole = false) {
     using P = typename Px<BPC>::pixel;
     constexpr int B = BPC / 8;
-    if (!b || b->layout < 1 || b->layout > 3 || !b->scratch) return -1;
-    for (int p = 0; p < 3; p++)
+    if (!b || b->layout < 0 || b->layout > 3 || !b->scratch) return -1;
+    const int np = b->layout ? 3 : 1;
+    for (int p = 0; p < np; p++)
         if (!b->in[p].data || !b->out[p].data) return -1;
     const int w = b->in[0].w, h = b->in[0].h;
     if (w <= 0 || h <= 0) return -1;
-    GrainArgs g;
-    memset(&g, 0, sizeof(g));
-    g.d = b->data;
-    g.layout = b->layout;
-    g.bdmax = BPC == 8 ? 255 : b->bitdepth_max;
-    g.grain = (int16_t *)b->scratch;
-    g.scaling = (uint8_t *)b->scratch + 3 * kGH * kGW * 2;
-    if (g.d.ar_coeff_lag < 0 || g.d.ar_coeff_lag > 3 || g.d.num_y_points > 14 || g.d.num_uv_points[0] > 10 ||
-        g.d.num_uv_points[1] > 10)
-        return -1;
-    k_grain_prep<<<1, 256, 0, stream>>>(g);
+    if (r0 < 0 || r0 >= r1 || r1 > (h + 31) / 32) return -1;
     ApplyArgs<BPC> a;
     memset(&a, 0, sizeof(a));
-    for (int p = 0; p < 3; p++) {
+    for (int p = 0; p < np; p++) {
         a.in[p] = (const P *)b->in[p].data;
         a.out[p] = (P *)b->out[p].data;
         a.is[p] = (int)(b->in[p].stride / B);
@@ -470,25 +611,205 @@ static int launch_grain(const Dav1dGpuFilmGrainBatch *b, hipStream_t stream) {
     a.w = w;
     a.h = h;
     a.layout = b->layout;
-    a.bdmax = g.bdmax;
+    a.bdmax = BPC == 8 ? 255 : b->bitdepth_max;
     a.is_id = b->is_id;
+    a.row0 = r0;
+    a.nrows = r1 - r0;
     a.d = b->data;
-    a.grain = g.grain;
-    a.scaling = g.scaling;
-    const int nblk = ((w + 31) / 32) * ((h + 31) / 32);
-    const dim3 grid((unsigned)((nblk + 7) & ~7));
-    if (b->layout == 1) k_grain_apply<BPC, 1><<<grid, 256, 0, stream>>>(a);
-    else if (b->layout == 2) k_grain_apply<BPC, 2><<<grid, 256, 0, stream>>>(a);
-    else k_grain_apply<BPC, 3><<<grid, 256, 0, stream>>>(a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        fprintf(stderr, "dav1d-gpu: film grain launch failed: %s\n", hipGetErrorString(e));
-        return -3;
-    }
-    return 0;
+    a.grain = (const int16_t *)b->scratch;
+    a.scaling = (const uint8_t *)b->scratch + 3 * kGH * kGW * 2;
+    if (whole) launch_apply<BPC, kApplyPicture>(a, stream);
+    else launch_apply<BPC, kApplyRows>(a, stream);
+    return launch_failed("apply");
 }
 
+// bitfn(dav1d_apply_grain): prep, then every strip, on one stream
+template <int BPC>
+static int launch_grain(const Dav1dGpuFilmGrainBatch *b, hipStream_t stream) {
+    if (!b || b->layout < 1 || b->layout > 3 || !b->scratch) return -1;
+    for (int p = 0; p < 3; p++)
+        if (!b->in[p].data || !b->out[p].data) return -1;
+    const int h = b->in[0].h;
+    if (b->in[0].w <= 0 || h <= 0) return -1;
+    const int rc = launch_prep<BPC>(&b->data, b->layout, b->bitdepth_max, b->scratch, stream);
+    return rc ? rc : launch_rows<BPC>(b, 0, (h + 31) / 32, stream, true);
+}
+
+// ---- per-call tier -------------------------------------------------------
+// Dav1dFilmGrainDSPContext (src/filmgrain.h:46-80) on the kernels above:
+// generate_grain_* is the prep body for one plane, fgy / fguv the apply
+// kernel on one staged strip with the caller's LUTs.
+template <int BPC> struct FgEntry { using type = int8_t; };
+template <> struct FgEntry<16> { using type = int16_t; };
+
+static bool fg_data_ok(const Dav1dGpuFilmGrainData *d) {
+    return d && d->ar_coeff_lag >= 0 && d->ar_coeff_lag <= 3;
+}
+
+// generate_grain_y (p == 0) / generate_grain_uv[layout - 1] (p == 1 + uv)
+template <int BPC>
+static bool fg_gen_t(typename FgEntry<BPC>::type (*buf)[kGW], const typename FgEntry<BPC>::type (*buf_y)[kGW],
+                     const Dav1dGpuFilmGrainData *data, int p, int layout, int bdmax) {
+    using E = typename FgEntry<BPC>::type;
+    constexpr long EB = sizeof(E);
+    if (!buf || !fg_data_ok(data) || p < 0 || p > 2 || (p && !buf_y)) return false;
+    const int sx = layout != 3, sy = layout == 1;
+    const int cw = p && sx ? 44 : kGW, ch = p && sy ? 38 : kGH;
+    const bool luma_term = p && data->num_y_points;   // filmgrain_tmpl.c:115-128
+    Stager st;
+    const int iy = luma_term ? st.in1(buf_y, kGH * kGW * EB) : -1;
+    const int ob = st.out(buf, kGW * EB, 0, cw * EB, 0, ch);
+    if (!st.upload()) return false;
+    GrainArgs g;
+    memset(&g, 0, sizeof(g));
+    g.d = *data;
+    g.layout = layout;
+    g.bdmax = bdmax;
+    k_grain_gen<E><<<1, 64, 0, st.stream()>>>(g, p, iy >= 0 ? st.origin<const E>(iy) : nullptr, st.origin<E>(ob),
+                                             (int)(st.pitch(ob) / EB));
+    return st.finish();
+}
+
+// fgy_32x32xn (layout 0: luma) / fguv_32x32xn[layout - 1] (plane 1 + uv) for
+// one strip: row_num gives the seeds and the overlap with the previous strip,
+// the pointers start at the strip's first row.
+template <int BPC>
+static bool fg_apply_t(int layout, typename Px<BPC>::pixel *dst, const typename Px<BPC>::pixel *src,
+                       ptrdiff_t stride, const Dav1dGpuFilmGrainData *data, size_t pw_, const uint8_t *scaling,
+                       const typename FgEntry<BPC>::type (*lut)[kGW], int bh, int row_num,
+                       const typename Px<BPC>::pixel *luma, ptrdiff_t luma_stride, int uv, int is_id, int bdmax) {
+    using P = typename Px<BPC>::pixel;
+    constexpr long B = sizeof(P);
+    constexpr int SC = BPC == 8 ? 256 : 4096;
+    const int sx = layout && layout != 3, sy = layout == 1;
+    const int pl = layout ? 1 + uv : 0;
+    if (!dst || !src || !data || !scaling || !lut || (layout && !luma) || uv < 0 || uv > 1 || row_num < 0 ||
+        pw_ == 0 || pw_ > (size_t)(1 << 16) || bh <= 0 || bh > (32 >> sy))
+        return false;
+    const int pw = (int)pw_;
+    // the kernel samples int16 [73][82] LUTs: 8 bpc entries are widened here
+    int16_t wide[BPC == 8 ? kGH * kGW : 1];
+    if (BPC == 8)
+        for (int i = 0; i < kGH * kGW; i++) wide[i] = (&lut[0][0])[i];
+    Stager st;
+    const int is = st.in(src, stride, 0, pw * B, 0, bh);
+    const int od = st.out(dst, stride, 0, pw * B, 0, bh);
+    // luma rows y << ss_ver, columns 2x and 2x + 1 (filmgrain_tmpl.c:286-300)
+    const int il = layout ? st.in(luma, luma_stride, 0, ((long)pw << sx) * B, 0, ((bh - 1) << sy) + 1) : -1;
+    const int ig = BPC == 8 ? st.in1(wide, sizeof(wide)) : st.in1(lut, kGH * kGW * 2);
+    const int ic = st.in1(scaling, SC);
+    if (!st.upload()) return false;
+    ApplyArgs<BPC> a;
+    memset(&a, 0, sizeof(a));
+    a.in[pl] = st.origin<const P>(is);
+    a.is[pl] = (int)(st.pitch(is) / B);
+    a.out[pl] = st.origin<P>(od);
+    a.os[pl] = (int)(st.pitch(od) / B);
+    if (layout) {
+        a.in[0] = st.origin<const P>(il);
+        a.is[0] = (int)(st.pitch(il) / B);
+    }
+    a.w = pw << sx;
+    a.h = row_num * 32 + (bh << sy);
+    a.layout = layout;
+    a.bdmax = bdmax;
+    a.is_id = is_id;
+    a.row0 = row_num;
+    a.nrows = 1;
+    a.plane = pl;
+    a.d = *data;
+    // the entry always adds grain (the reference's caller skips planes without
+    // points, fg_apply_tmpl.c:180-222); the kernel would copy such a plane
+    if (!pl && !a.d.num_y_points) a.d.num_y_points = 1;
+    if (pl && !a.d.chroma_scaling_from_luma && !a.d.num_uv_points[uv]) a.d.num_uv_points[uv] = 1;
+    a.call_grain = st.origin<const int16_t>(ig);
+    a.call_scaling = st.origin<const uint8_t>(ic);
+    launch_apply<BPC, kApplyCall>(a, st.stream());
+    return st.finish();
+}
+
+static Dav1dFilmGrainDSPContext_8bpc g_fb8;
+static Dav1dFilmGrainDSPContext_16bpc g_fb16;
+
+#define FG_ENTRIES(BPC, P, E, BDP, BDV)                                                                       \
+static void fg_gen_y_##BPC(E buf[][kGW], const Dav1dGpuFilmGrainData *d BDP)                                 \
+{ DGPU_OR_FALLBACK((fg_gen_t<BPC>(buf, nullptr, d, 0, 1, BDV)), g_fb##BPC.generate_grain_y, buf,              \
+                   d BDV##_ARG); }                                                                            \
+template <int L>                                                                                              \
+static void fg_gen_uv_##BPC(E buf[][kGW], const E buf_y[][kGW], const Dav1dGpuFilmGrainData *d,               \
+                            intptr_t uv BDP)                                                                  \
+{ DGPU_OR_FALLBACK((fg_gen_t<BPC>(buf, buf_y, d, 1 + (int)(uv != 0), L, BDV)),                                \
+                   g_fb##BPC.generate_grain_uv[L - 1], buf, buf_y, d, uv BDV##_ARG); }                        \
+static void fg_y_##BPC(P *dst, const P *src, ptrdiff_t s, const Dav1dGpuFilmGrainData *d, size_t pw,         \
+                       const uint8_t *sc, const E lut[][kGW], int bh, int row BDP)                           \
+{ DGPU_OR_FALLBACK((fg_apply_t<BPC>(0, dst, src, s, d, pw, sc, lut, bh, row, nullptr, 0, 0, 0, BDV)),        \
+                   g_fb##BPC.fgy_32x32xn, dst, src, s, d, pw, sc, lut, bh, row BDV##_ARG); }                  \
+template <int L>                                                                                              \
+static void fg_uv_##BPC(P *dst, const P *src, ptrdiff_t s, const Dav1dGpuFilmGrainData *d, size_t pw,        \
+                        const uint8_t *sc, const E lut[][kGW], int bh, int row, const P *luma,               \
+                        ptrdiff_t ls, int uv, int is_id BDP)                                                  \
+{ DGPU_OR_FALLBACK((fg_apply_t<BPC>(L, dst, src, s, d, pw, sc, lut, bh, row, luma, ls, uv, is_id, BDV)),     \
+                   g_fb##BPC.fguv_32x32xn[L - 1], dst, src, s, d, pw, sc, lut, bh, row, luma, ls, uv,         \
+                   is_id BDV##_ARG); }
+
+#define BD8_PARAM
+#define BD8_VAL 255
+#define BD8_VAL_ARG
+#define BD16_PARAM , int bitdepth_max
+#define BD16_VAL bitdepth_max
+#define BD16_VAL_ARG , bitdepth_max
+FG_ENTRIES(8, uint8_t, int8_t, BD8_PARAM, BD8_VAL)
+FG_ENTRIES(16, uint16_t, int16_t, BD16_PARAM, BD16_VAL)
+
+#define FILL_FG(BPC, c)                                   \
+    do {                                                  \
+        c->generate_grain_y = fg_gen_y_##BPC;             \
+        c->generate_grain_uv[0] = fg_gen_uv_##BPC<1>;     \
+        c->generate_grain_uv[1] = fg_gen_uv_##BPC<2>;     \
+        c->generate_grain_uv[2] = fg_gen_uv_##BPC<3>;     \
+        c->fgy_32x32xn = fg_y_##BPC;                      \
+        c->fguv_32x32xn[0] = fg_uv_##BPC<1>;              \
+        c->fguv_32x32xn[1] = fg_uv_##BPC<2>;              \
+        c->fguv_32x32xn[2] = fg_uv_##BPC<3>;              \
+    } while (0)
+
 }  // namespace dgpu
+
+using namespace dgpu;
+
+// bitfn(dav1d_film_grain_dsp_init) replacement, src/filmgrain_tmpl.c:423-441
+// The _gpu_ hooks keep the caller's previous entries as fallbacks.
+extern "C" void dav1d_film_grain_dsp_init_gpu_8bpc(Dav1dFilmGrainDSPContext_8bpc *c) {
+    Dav1dFilmGrainDSPContext_8bpc g{}, *gp = &g;
+    FILL_FG(8, gp);
+    save_fallback(&g_fb8, c, gp);
+    FILL_FG(8, c);
+}
+extern "C" void dav1d_film_grain_dsp_init_gpu_16bpc(Dav1dFilmGrainDSPContext_16bpc *c) {
+    Dav1dFilmGrainDSPContext_16bpc g{}, *gp = &g;
+    FILL_FG(16, gp);
+    save_fallback(&g_fb16, c, gp);
+    FILL_FG(16, c);
+}
+extern "C" void dav1d_film_grain_dsp_init_8bpc(Dav1dFilmGrainDSPContext_8bpc *c) { FILL_FG(8, c); }
+extern "C" void dav1d_film_grain_dsp_init_16bpc(Dav1dFilmGrainDSPContext_16bpc *c) { FILL_FG(16, c); }
+
+extern "C" int dav1d_gpu_prep_grain_8bpc(const Dav1dGpuFilmGrainData *data, int layout, int bitdepth_max,
+                                         void *scratch, void *stream) {
+    return launch_prep<8>(data, layout, bitdepth_max, scratch, (hipStream_t)stream);
+}
+extern "C" int dav1d_gpu_prep_grain_16bpc(const Dav1dGpuFilmGrainData *data, int layout, int bitdepth_max,
+                                          void *scratch, void *stream) {
+    return launch_prep<16>(data, layout, bitdepth_max, scratch, (hipStream_t)stream);
+}
+extern "C" int dav1d_gpu_apply_grain_rows_8bpc(const Dav1dGpuFilmGrainBatch *b, int row_start, int row_end,
+                                               void *stream) {
+    return launch_rows<8>(b, row_start, row_end, (hipStream_t)stream);
+}
+extern "C" int dav1d_gpu_apply_grain_rows_16bpc(const Dav1dGpuFilmGrainBatch *b, int row_start, int row_end,
+                                                void *stream) {
+    return launch_rows<16>(b, row_start, row_end, (hipStream_t)stream);
+}
 
 extern "C" int dav1d_gpu_apply_grain_8bpc(const Dav1dGpuFilmGrainBatch *b, void *stream) {
     return dgpu::launch_grain<8>(b, (hipStream_t)stream);

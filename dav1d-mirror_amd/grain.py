@@ -5,7 +5,9 @@ Dav1dGpuFilmGrainBatch): bitfn(dav1d_apply_grain) (src/fg_apply_tmpl.c:
 `make_grain_data` draws film grain parameters over the ranges the
 reference's checkasm uses (tests/checkasm/filmgrain.c:59-330); `GrainCase`
 is a random picture plus parameters; `DeviceGrain` runs
-dav1d_gpu_apply_grain_{8,16}bpc on it.
+dav1d_gpu_apply_grain_{8,16}bpc on it, or the split entries a decoder uses:
+dav1d_gpu_prep_grain_* once (`launch_prep`, any stream) and
+dav1d_gpu_apply_grain_rows_* per range of 32-row strips (`launch_rows`).
 """
 import ctypes
 from dataclasses import dataclass
@@ -61,10 +63,10 @@ def make_grain_data(rng, lag=None, csfl=None, num_y=None, num_uv=(None, None), o
 class GrainCase:
     bpc: int
     bitdepth_max: int
-    layout: int          # 1 I420, 2 I422, 3 I444
+    layout: int          # 0 I400 (split entries only), 1 I420, 2 I422, 3 I444
     is_id: int
     data: abi.FilmGrainData
-    planes: list         # 3 (h, w) pixel arrays (the reconstructed picture)
+    planes: list         # 3 (h, w) pixel arrays (the reconstructed picture); 1 for I400
 
     @property
     def plane_wh(self):
@@ -76,7 +78,7 @@ def make_grain_case(seed=1, width=256, height=128, bpc=8, bitdepth_max=255, layo
     bdmax = 255 if bpc == 8 else bitdepth_max
     sx, sy = int(layout != 3), int(layout == 1)
     pdt = np.uint8 if bpc == 8 else np.uint16
-    whs = [(width, height)] + [((width + sx) >> sx, (height + sy) >> sy)] * 2
+    whs = [(width, height)] + [((width + sx) >> sx, (height + sy) >> sy)] * (2 if layout else 0)
     planes = [rng.integers(0, bdmax + 1, (h, w)).astype(pdt) for (w, h) in whs]
     return GrainCase(bpc, bdmax, layout, int(rng.integers(0, 2)), make_grain_data(rng, **kw), planes)
 
@@ -114,6 +116,33 @@ class DeviceGrain:
         rc = fn(ctypes.byref(self.batch), ctypes.c_void_p(s.cuda_stream))
         if rc:
             raise RuntimeError(f"dav1d_gpu_apply_grain failed: {rc}")
+
+    def _sfx(self):
+        return f"{8 if self.case.bpc == 8 else 16}bpc"
+
+    def launch_prep(self, stream=None):
+        """The grain and scaling LUTs into the scratch (dav1d_gpu_prep_grain_*):
+        needs only the parameters, so any stream, as early as the frame header."""
+        s = stream if stream is not None else self.torch.cuda.current_stream()
+        c = self.case
+        rc = getattr(self.lib, "dav1d_gpu_prep_grain_" + self._sfx())(
+            ctypes.byref(self.batch.data), c.layout, c.bitdepth_max, self.batch.scratch,
+            ctypes.c_void_p(s.cuda_stream))
+        if rc:
+            raise RuntimeError(f"dav1d_gpu_prep_grain failed: {rc}")
+
+    def launch_rows(self, r0, r1, stream=None):
+        """The 32-luma-row strips [r0, r1) (dav1d_gpu_apply_grain_rows_*), with
+        the LUTs a finished launch_prep left in the scratch."""
+        s = stream if stream is not None else self.torch.cuda.current_stream()
+        rc = getattr(self.lib, "dav1d_gpu_apply_grain_rows_" + self._sfx())(
+            ctypes.byref(self.batch), r0, r1, ctypes.c_void_p(s.cuda_stream))
+        if rc:
+            raise RuntimeError(f"dav1d_gpu_apply_grain_rows failed: {rc}")
+
+    @property
+    def strips(self):
+        return (self.case.planes[0].shape[0] + 31) // 32
 
     def outputs_host(self):
         return [t.cpu().numpy().view(np.uint16) if self.case.bpc != 8 else t.cpu().numpy() for t in self.outs]

@@ -1014,7 +1014,9 @@ typedef struct Dav1dGpuFilmGrainBatch {
     Dav1dGpuPlane out[3];    /* device: the output picture (planes without
                                 grain are copied), distinct from `in`        */
     Dav1dGpuFilmGrainData data;
-    int32_t layout;          /* DAV1D_PIXEL_LAYOUT_*: 1 I420, 2 I422, 3 I444  */
+    int32_t layout;          /* DAV1D_PIXEL_LAYOUT_*: 1 I420, 2 I422, 3 I444;
+                                0 I400 with dav1d_gpu_apply_grain_rows_* only
+                                (in[1..2] / out[1..2] may then be NULL)       */
     int32_t bitdepth_max;
     int32_t is_id;           /* seq_hdr->mtrx == DAV1D_MC_IDENTITY           */
     int32_t pad_;
@@ -1022,9 +1024,96 @@ typedef struct Dav1dGpuFilmGrainBatch {
 } Dav1dGpuFilmGrainBatch;
 
 /* in[0].w / h give the picture size.  Errors: -1 NULL / bad layout /
- * missing scratch, -3 launch failure. */
+ * missing scratch / ar_coeff_lag outside 0..3 / point counts above 14 (luma)
+ * or 10 (chroma) and, since the split below, negative point counts too (the
+ * kernel would read before the point lists); -3 launch failure. */
 int dav1d_gpu_apply_grain_8bpc(const Dav1dGpuFilmGrainBatch *b, void *stream);
 int dav1d_gpu_apply_grain_16bpc(const Dav1dGpuFilmGrainBatch *b, void *stream);
+
+/* The same work as a decoder schedules it (src/fg_apply.h: dav1d_prep_grain
+ * once per picture, dav1d_apply_grain_row per 32-row strip as rows become
+ * final); dav1d_gpu_apply_grain_* above is prep followed by every strip.
+ *
+ * prep_grain: the prep launch alone.  It reads only `data` (copied at the
+ * call) and writes the grain and scaling LUTs into `scratch`
+ * (DGPU_GRAIN_SCRATCH_BYTES, the layout above); it touches no picture, so it
+ * can run on any stream as soon as the frame header is parsed.  The strips
+ * must be ordered behind it (an event, or the same stream).  layout 0..3;
+ * with layout 0 (I400) the chroma parameters in `data` are ignored and the
+ * chroma grain LUTs and scaling[1], scaling[2] are written as zeros.
+ * bitdepth_max is ignored at 8 bpc.  Errors: -1 NULL data / scratch, bad
+ * layout, ar_coeff_lag outside 0..3 or point counts outside 0..14 (luma) /
+ * 0..10 (chroma); -3 launch failure. */
+int dav1d_gpu_prep_grain_8bpc(const Dav1dGpuFilmGrainData *data, int layout,
+                              int bitdepth_max, void *scratch, void *stream);
+int dav1d_gpu_prep_grain_16bpc(const Dav1dGpuFilmGrainData *data, int layout,
+                               int bitdepth_max, void *scratch, void *stream);
+/* apply_grain_rows: the apply launch alone, for the 32-luma-row strips
+ * [row_start, row_end) -- the `row` of dav1d_apply_grain_row
+ * (src/fg_apply_tmpl.c:161-223) -- with the LUTs a finished prep_grain of the
+ * same data, layout and bit depth left in b->scratch.  0 <= row_start <
+ * row_end <= (in[0].h + 31) / 32, anything else returns -1.  Strip r reads
+ * luma rows [32 r, 32 r + 32) of `in` and the chroma rows under them, and
+ * writes the same rows of `out`; pixels outside the range are not written.
+ * A strip reads no pixel of another strip (the overlap blend uses the
+ * previous strip's random offsets, recomputed from the seed, not its
+ * pixels), so ranges may run in any order, each as soon as its `in` rows are
+ * final.
+ *   Difference from the reference: dav1d_prep_grain copies a plane without
+ * grain whole (:128-158).  A device caller's later rows do not exist yet
+ * when prep runs, so here apply_grain_rows copies such a plane for the rows
+ * of its range; after every strip has run the pictures are the same.
+ *   b->layout 0 (I400): luma only, in[1..2] and out[1..2] may be NULL;
+ * 1..3 as dav1d_gpu_apply_grain_*.  Errors: -1 NULL / bad layout / missing
+ * scratch or plane / bad range, -3 launch failure. */
+int dav1d_gpu_apply_grain_rows_8bpc(const Dav1dGpuFilmGrainBatch *b,
+                                    int row_start, int row_end, void *stream);
+int dav1d_gpu_apply_grain_rows_16bpc(const Dav1dGpuFilmGrainBatch *b,
+                                     int row_start, int row_end, void *stream);
+
+/* Per-call tier: Dav1dFilmGrainDSPContext (src/filmgrain.h:46-80), the
+ * seventh member of Dav1dDSPContext, with the reference's init hook name
+ * bitfn(dav1d_film_grain_dsp_init) (src/filmgrain_tmpl.c:423-441).  `entry`
+ * is int8_t at 8 bpc and int16_t at 16 bpc, `scaling` holds 256 entries at
+ * 8 bpc and 4096 at 16 bpc; generate_grain_uv / fguv_32x32xn are indexed by
+ * layout - 1.  Synchronous, with the error contract of the other tables.
+ *   generate_grain_y writes buf[0..72][0..81]; generate_grain_uv writes rows
+ * [0, 38 or 73) by columns [0, 44 or 82) (subsampled or not,
+ * filmgrain_tmpl.c:100-108) and reads buf_y; the rest of the caller's
+ * [74][82] buffer is left untouched.  fgy_32x32xn / fguv_32x32xn filter one
+ * strip of bh rows by pw pixels: row_num seeds the strip and selects the
+ * overlap with the previous one, the pointers start at the strip's first
+ * row.  fguv reads luma_row at 2x and 2x + 1 (4:2:0, 4:2:2) of every
+ * (y << ss_ver)-th row as the reference does (:286-300): for an odd luma
+ * width the caller pads luma_row[w] = luma_row[w - 1] first, as
+ * dav1d_apply_grain_row does (fg_apply_tmpl.c:195-202). */
+#define DGPU_FG_TYPES(sfx, pixel, entry, SCALING, HBD)                             \
+typedef void (*dgpu_generate_grain_y_fn_##sfx)(entry buf[][DGPU_GRAIN_W],         \
+    const Dav1dGpuFilmGrainData *data HBD);                                       \
+typedef void (*dgpu_generate_grain_uv_fn_##sfx)(entry buf[][DGPU_GRAIN_W],        \
+    const entry buf_y[][DGPU_GRAIN_W], const Dav1dGpuFilmGrainData *data,         \
+    intptr_t uv HBD);                                                             \
+typedef void (*dgpu_fgy_32x32xn_fn_##sfx)(pixel *dst_row, const pixel *src_row,   \
+    ptrdiff_t stride, const Dav1dGpuFilmGrainData *data, size_t pw,               \
+    const uint8_t scaling[SCALING], const entry grain_lut[][DGPU_GRAIN_W],        \
+    int bh, int row_num HBD);                                                     \
+typedef void (*dgpu_fguv_32x32xn_fn_##sfx)(pixel *dst_row, const pixel *src_row,  \
+    ptrdiff_t stride, const Dav1dGpuFilmGrainData *data, size_t pw,               \
+    const uint8_t scaling[SCALING], const entry grain_lut[][DGPU_GRAIN_W],        \
+    int bh, int row_num, const pixel *luma_row, ptrdiff_t luma_stride,            \
+    int uv_pl, int is_id HBD);                                                    \
+typedef struct Dav1dFilmGrainDSPContext_##sfx {                                   \
+    dgpu_generate_grain_y_fn_##sfx generate_grain_y;                              \
+    dgpu_generate_grain_uv_fn_##sfx generate_grain_uv[3];   /* 420, 422, 444 */   \
+    dgpu_fgy_32x32xn_fn_##sfx fgy_32x32xn;                                        \
+    dgpu_fguv_32x32xn_fn_##sfx fguv_32x32xn[3];                                   \
+} Dav1dFilmGrainDSPContext_##sfx;
+DGPU_FG_TYPES(8bpc, uint8_t, int8_t, 256, DGPU_HBD_NONE)
+DGPU_FG_TYPES(16bpc, uint16_t, int16_t, 4096, DGPU_HBD_ARG)
+void dav1d_film_grain_dsp_init_8bpc(Dav1dFilmGrainDSPContext_8bpc *c);
+void dav1d_film_grain_dsp_init_16bpc(Dav1dFilmGrainDSPContext_16bpc *c);
+void dav1d_film_grain_dsp_init_gpu_8bpc(Dav1dFilmGrainDSPContext_8bpc *c);
+void dav1d_film_grain_dsp_init_gpu_16bpc(Dav1dFilmGrainDSPContext_16bpc *c);
 
 /* ---- CDEF (the first post-filter) -----------------------
  * Per-call tier: Dav1dCdefDSPContext (src/cdef.h:64-67; decl_cdef_fn :53-58,
